@@ -12,14 +12,20 @@ with num_action_repeats=1 (common/common_flags.py:43; learner.py:236-237).
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
 
-The default single-GPU run also reports, outside the timed region and in the same JSON line:
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when --dump-outputs DIR is given
+(DIR/<name>.npy: the loss and logged scalars the step returns, the updated parameters and the step's gradients), and
+prints the JSON line.  --full adds, outside the timed region and in the same JSON line:
+  roofline       per-kernel attribution pass (serialized HIP events), dominant kernel, whole-step roofline
+  windows        --windows timed windows of K steps each (median / min / max)
+  exchange       N > 1: the same steps without the all-reduce (exposed exchange time)
+  vtrace         V-trace max-abs-err vs the oracle and the reference code's outputs, HBM sweep of the scan
   parity         one train step at the bench shape against the CPU oracle (tests/parity.py)
   other_configs  BASELINE configs[2] (DMLab ImpalaDeep+LSTM) and configs[4] (R2D2), a few steps each
   inference      central-inference step (learner.py:350-405) at n = 64 / 256 / 1024
   serving        inference and training together on the one GPU, without and with the native gRPC transport
   ingest         the same step with the NEXT unroll's host->device copy in flight on its own stream
   cpu_baseline   the oracle's eager PyTorch-CPU learner step on the host cores
-(--quick skips them.)
+(--full --quick keeps the first four and skips the rest.)
 """
 import argparse
 import gc
@@ -81,10 +87,17 @@ def parse():
                   help='run the N-replica launch mode (graph segments, asynchronous range all-reduces on the collective '
                        'stream, update graph) even with ONE rank: the RCCL rehearsal of the multi-GPU line on a 1-GPU box')
   ap.add_argument('--windows', type=int, default=6,
-                  help='timed windows of --steps steps each: the first is the contract\'s (value), all of them give the '
-                       'median / min / max of the line\'s `windows` record')
+                  help='--full: timed windows of --steps steps each: the first is the contract\'s (value), all of them give '
+                       'the median / min / max of the line\'s `windows` record (a plain run times one window)')
   ap.add_argument('--quick', action='store_true',
-                  help='only the timed learner step: no parity / other_configs / inference / ingest / cpu_baseline records')
+                  help='with --full: only the timed learner step and its attribution: no parity / other_configs / '
+                       'inference / ingest / cpu_baseline records')
+  ap.add_argument('--full', action='store_true',
+                  help='everything beyond the headline figure: roofline / attribution pass, extra windows, exposed '
+                       'exchange, V-trace checks, parity, other configs, inference, serving, ingest, CPU baseline')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / '
+                       'float64, at most 64 MB in all)')
   return ap.parse_args()
 
 
@@ -224,9 +237,47 @@ def build_workload(config, torso, T, B, A, dev, reduction, graph, world, seed, f
   return agent, lrn, unroll, extra, workload
 
 
+MAX_DUMP_ELEMS = 6 << 20      # per array: a larger one is written as a fixed, seeded sample of this many elements
+
+
+def step_outputs(config, out, agent, mode):
+  """name -> host array (float32 / float64) of what one learner step hands its caller: the loss and the logged scalars
+  (R2D2: the new priorities and the gradient norm), plus the parameters it updated and the gradients it applied."""
+  res = {}
+
+  def put(name, t):
+    a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+    res[name] = a.astype(a.dtype if a.dtype in (np.float32, np.float64) else np.float64)
+  put('loss', out[0])
+  if config == 'r2d2':
+    put('priorities', out[1])
+    put('grad_norm', out[2] if mode == 'eager' else torch.sqrt(out[2][0]))    # the graph hands back the sum of squares
+  else:
+    for k, v in out[1].items():
+      put('log_' + ''.join(c if c.isalnum() else '_' for c in k), v)
+  put('params', agent.flat.params)
+  put('grads', agent.flat.grads)
+  for k, a in list(res.items()):
+    if a.size > MAX_DUMP_ELEMS:
+      idx = np.sort(np.random.default_rng(0).choice(a.size, MAX_DUMP_ELEMS, replace=False))
+      res[k] = a.reshape(-1)[idx]
+  return res
+
+
+def write_outputs(d, arrays):
+  os.makedirs(d, exist_ok=True)
+  total = sum(a.nbytes for a in arrays.values())
+  assert total <= 64e6, total
+  for k, a in arrays.items():
+    np.save(os.path.join(d, k + '.npy'), a)
+
+
 def run_learner(config, steps, warmup, dev, rank=0, world=1, distributed=False, torso='shallow', batch=0, unroll_len=0,
-                actions=0, reduction='mean', graph=1, attribution_steps=3, force_exchange=False, extra_windows=0):
-  """Times `steps` learner steps of one BASELINE config; returns the record the JSON line is built from."""
+                actions=0, reduction='mean', graph=1, attribution_steps=3, force_exchange=False, extra_windows=0,
+                full=True, want_outputs=False):
+  """Times `steps` learner steps of one BASELINE config; returns the record the JSON line is built from.
+  full=False: only warm-up and the timed steps (no attribution pass, extra windows, exposed exchange or roofline);
+  want_outputs: the record carries step_outputs() of the last timed step under 'outputs'."""
   from seed_rl_amd import learner, ops
   T = unroll_len or (120 if config == 'r2d2' else 20)
   B = batch or (256 if config in ('dmlab', 'r2d2') else 512)
@@ -240,40 +291,43 @@ def run_learner(config, steps, warmup, dev, rank=0, world=1, distributed=False, 
     torch.cuda.synchronize()
 
   # ---- warmup, then the per-kernel attribution pass: the device is drained before every region, i.e. every kernel
-  # is timed the way rocprofv3 times it (serialised dispatches) -- profiles/*_kernel_stats.csv is the same view ----
+  # is timed the way rocprofv3 times it (serialised dispatches) -- profiles/*_kernel_stats.csv is the same view.
+  # Without --full the same number of eager steps runs unprofiled: the timed steps start from the same state ----
   for _ in range(max(warmup - attribution_steps, 1 if warmup else 0)):
     lrn.minimize(unroll, *extra)
   prof_all = ops.Profiler(serialize=True)
-  ops.set_profiler(prof_all)
+  if full:
+    ops.set_profiler(prof_all)
   for _ in range(min(attribution_steps, max(warmup, 1))):
     lrn.minimize(unroll, *extra)
   ops.set_profiler(None)
-  kern = prof_all.summary()
-  # what an event pair around ONE dispatch on a drained device reads for a kernel that does (almost) nothing: the
-  # dispatch latency of an idle queue sits inside every serialized region above and not inside rocprofv3's kernel
-  # durations (r6: stack_conv_fwd 139.1 us by events, 130.0 us in the kernel trace of the same box)
-  tiny = torch.zeros(64, device=dev)
-  floor_ms = []
-  for _ in range(20):
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(); tiny.add_(1.0); e1.record()
-    torch.cuda.synchronize()
-    floor_ms.append(e0.elapsed_time(e1))
-  dispatch_floor_ms = float(np.median(floor_ms))
-  nattr = min(attribution_steps, max(warmup, 1))
-  for v in kern.values():
-    v['total_ms'] /= nattr; v['calls'] /= nattr    # (true division in both places: step_roofline prices group calls)
-    for g in v['groups']:
-      g['calls'] /= nattr
-  # dominant kernel = largest share of the step in that pass (averaged over the attribution steps so that two kernels
-  # a few microseconds apart do not swap places between runs), among the MFMA kernels and the HBM kernels that move
-  # >= 32 MB, averaging >= 50 us per launch and launched at most 64 times per step: event pairs around
-  # few-microsecond kernels launched hundreds of times per step are not a reliable ranking
-  big = [k for k in kern if (kern[k]['flops'] > 0 or kern[k]['bytes'] >= (1 << 25)) and kern[k]['avg_ms'] >= 0.05
-         and kern[k]['calls'] <= 64]
-  big = big or list(kern)
-  dominant = max(big, key=lambda k: kern[k]['total_ms'])
+  if full:
+    kern = prof_all.summary()
+    # what an event pair around ONE dispatch on a drained device reads for a kernel that does (almost) nothing: the
+    # dispatch latency of an idle queue sits inside every serialized region above and not inside rocprofv3's kernel
+    # durations (r6: stack_conv_fwd 139.1 us by events, 130.0 us in the kernel trace of the same box)
+    tiny = torch.zeros(64, device=dev)
+    floor_ms = []
+    for _ in range(20):
+      torch.cuda.synchronize()
+      e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+      e0.record(); tiny.add_(1.0); e1.record()
+      torch.cuda.synchronize()
+      floor_ms.append(e0.elapsed_time(e1))
+    dispatch_floor_ms = float(np.median(floor_ms))
+    nattr = min(attribution_steps, max(warmup, 1))
+    for v in kern.values():
+      v['total_ms'] /= nattr; v['calls'] /= nattr    # (true division in both places: step_roofline prices group calls)
+      for g in v['groups']:
+        g['calls'] /= nattr
+    # dominant kernel = largest share of the step in that pass (averaged over the attribution steps so that two kernels
+    # a few microseconds apart do not swap places between runs), among the MFMA kernels and the HBM kernels that move
+    # >= 32 MB, averaging >= 50 us per launch and launched at most 64 times per step: event pairs around
+    # few-microsecond kernels launched hundreds of times per step are not a reliable ranking
+    big = [k for k in kern if (kern[k]['flops'] > 0 or kern[k]['bytes'] >= (1 << 25)) and kern[k]['avg_ms'] >= 0.05
+           and kern[k]['calls'] <= 64]
+    big = big or list(kern)
+    dominant = max(big, key=lambda k: kern[k]['total_ms'])
 
   # ---- timed region: exactly K steps, barrier + sync on both sides ----
   step_fn = lambda: lrn.minimize(unroll, *extra)
@@ -298,8 +352,8 @@ def run_learner(config, steps, warmup, dev, rank=0, world=1, distributed=False, 
       if world > 1:
         raise                                    # ranks must not diverge into different launch modes
       gs, step_fn, mode = None, (lambda: lrn.minimize(unroll, *extra)), 'eager'
-  prof = ops.Profiler(only=[dominant])
-  if mode == 'eager':
+  prof = ops.Profiler(only=[dominant]) if full else None
+  if mode == 'eager' and full:
     ops.set_profiler(prof)
   barrier()
   t0 = time.perf_counter()
@@ -309,11 +363,12 @@ def run_learner(config, steps, warmup, dev, rank=0, world=1, distributed=False, 
   dt = time.perf_counter() - t0
   ops.set_profiler(None)
   loss = out[0]
-  # The contract's window above is what `value` / `ms_per_step` are computed from.  Behind it, extra_windows more windows
-  # of the SAME K steps with the same brackets: boxes of the pool differ by up to 18 % and one 19 ms window says nothing
-  # about its own spread -- the line carries median / min / max over all of them.
+  outputs = step_outputs(config, out, agent, mode) if want_outputs else None
+  # The contract's window above is what `value` / `ms_per_step` are computed from.  Behind it (--full), extra_windows more
+  # windows of the SAME K steps with the same brackets: boxes of the pool differ by up to 18 % and one 19 ms window says
+  # nothing about its own spread -- the line carries median / min / max over all of them.
   window_ms = [dt / steps * 1e3]
-  for _ in range(extra_windows if mode != 'eager' else 0):
+  for _ in range(extra_windows if mode != 'eager' and full else 0):
     barrier()
     tw = time.perf_counter()
     for _ in range(steps):
@@ -324,7 +379,7 @@ def run_learner(config, steps, warmup, dev, rank=0, world=1, distributed=False, 
     wt = torch.tensor(window_ms, device=dev, dtype=torch.float64)
     torch.distributed.all_reduce(wt, op=torch.distributed.ReduceOp.MAX)
     window_ms = [float(x) for x in wt]
-  if mode != 'eager':
+  if mode != 'eager' and full:
     # free-running kernel time of the dominant kernel: HIP events around it on the launch stream, in a few eager
     # steps after the timed region (events cannot be recorded inside a replayed graph)
     ops.set_profiler(prof)
@@ -343,7 +398,7 @@ def run_learner(config, steps, warmup, dev, rank=0, world=1, distributed=False, 
     # is the last thing the run does with them).  exposed = (step with exchange) - (step without).
     bucket = agent.flat.grads.numel() * 4
     exposed = None
-    if gs is not None:
+    if gs is not None and full:
       gs.exchange = False
       for _ in range(2):
         step_fn()
@@ -367,6 +422,12 @@ def run_learner(config, steps, warmup, dev, rank=0, world=1, distributed=False, 
   assert np.isfinite(loss_val)
   if hasattr(agent, 'check_errors'):
     agent.check_errors()
+  rec = dict(T=T, B=B, A=A, workload=workload, mode=mode, params=agent.flat.num_params(), loss=loss_val,
+             ms_per_step=dt / steps * 1e3, frames_per_s=world * B * T / (dt / steps), exchange=exchange, outputs=outputs)
+  if not full:
+    del agent, lrn, unroll, extra
+    _release()
+    return rec
 
   free = prof.summary().get(dominant) or dict(avg_ms=0.0)
   d = kern[dominant]
@@ -401,14 +462,13 @@ def run_learner(config, steps, warmup, dev, rank=0, world=1, distributed=False, 
                   avg_kernel_ms_less_dispatch=round(max(d['avg_ms'] - dispatch_floor_ms, 0.0), 4),
                   frac_free_running=round(ach_free / peak, 4), avg_kernel_ms_free_running=round(free['avg_ms'], 4),
                   clock='HIP events on the launch stream; serialized = device drained before the kernel (rocprofv3 view)')
-  rec = dict(
-      T=T, B=B, A=A, workload=workload, mode=mode, params=agent.flat.num_params(), loss=loss_val,
-      ms_per_step=dt / steps * 1e3, frames_per_s=world * B * T / (dt / steps), roofline=roofline, dominant=dominant,
+  rec.update(
+      roofline=roofline, dominant=dominant,
       windows=dict(count=len(window_ms), steps_each=steps, ms_per_step=[round(x, 4) for x in window_ms],
                    median=round(float(np.median(window_ms)), 4), min=round(min(window_ms), 4), max=round(max(window_ms), 4),
                    note='window 0 is the contract\'s timed region (value / ms_per_step); the others repeat it'),
       step_roofline=step_roofline(kern, dt / steps * 1e3),
-      kernels_ms_per_step={k: round(v['total_ms'], 4) for k, v in kern.items()}, exchange=exchange,
+      kernels_ms_per_step={k: round(v['total_ms'], 4) for k, v in kern.items()},
       # the other MFMA kernels of the attribution pass (>= 50 us per launch), same (serialized) accounting as `roofline`
       mfma_kernels={
           k: dict(avg_ms=round(v['avg_ms'], 4), tflops=round(v['flops'] / (v['avg_ms'] * 1e-3) / 1e12, 1),
@@ -651,14 +711,16 @@ def main():
 
   rec = run_learner(args.config, args.steps, args.warmup, dev, rank, world, distributed, args.torso, args.batch,
                     args.unroll, args.actions, args.reduction, args.graph, force_exchange=args.force_exchange,
-                    extra_windows=args.windows - 1)
+                    extra_windows=args.windows - 1, full=args.full, want_outputs=bool(args.dump_outputs) and rank == 0)
+  if rec['outputs'] is not None:
+    write_outputs(args.dump_outputs, rec.pop('outputs'))
   T, B, A = rec['T'], rec['B'], rec['A']
-  roofline = rec['roofline']
+  roofline = rec.get('roofline')
   headline = args.config == 'atari' and args.torso == 'shallow' and B == 512 and T == 20 and A == 18
 
   # HBM traffic of the dominant kernel from the committed PMC passes (same config only; latest profiling round)
   tfiles = sorted(glob.glob(os.path.join(ROOT, 'profiles', 'r*_cfg2_traffic.json')))
-  if headline and tfiles:
+  if args.full and headline and tfiles:
     from seed_rl_amd import build as _build
     tj = json.load(open(tfiles[-1]))
     tb = tj['traffic_bytes']
@@ -690,24 +752,22 @@ def main():
                  'grad_reduction': args.reduction, 'params': rec['params'], 'launch': rec['mode'],
                  'ingest': 'resident (unroll in HBM before the timed region)',
                  'process_group': (('rccl' if args.backend == 'nccl' else 'gloo') if distributed else None)},
-      'windows': rec['windows'],
-      'roofline': roofline,
-      'step_roofline': rec['step_roofline'],
-      'exchange': rec['exchange'],
-      'loss': round(rec['loss'], 6),
-      'kernels_ms_per_step': rec['kernels_ms_per_step'],
-      'mfma_kernels': rec['mfma_kernels'],
   }
+  if args.full:
+    result.update(windows=rec['windows'], roofline=roofline, step_roofline=rec['step_roofline'])
+  result.update(exchange=rec['exchange'], loss=round(rec['loss'], 6))
+  if args.full:
+    result.update(kernels_ms_per_step=rec['kernels_ms_per_step'], mfma_kernels=rec['mfma_kernels'])
   if world > ndev:
     result['dry_run'] = ('%d ranks share %d device(s) over gloo: exercises the N-rank code path (sharded columns, graph '
                          'segments, overlapped exchange, update graph); the throughput is NOT a scaling measurement'
                          % (world, ndev))
-  if world == 1:
+  if world == 1 and args.full:
     err, err_ref, sweep = vtrace_checks(dev)
     result['vtrace_max_abs_err'] = err
     result['vtrace_max_abs_err_vs_reference_code'] = err_ref
     result['vtrace_scan_hbm'] = sweep
-  if world == 1 and not args.quick:
+  if world == 1 and args.full and not args.quick:
     from tests import parity
     # one train step at the bench shape against the CPU oracle (outside the timed region; same code as
     # tests/test_gpu_fullsize.py)
@@ -779,7 +839,7 @@ def main():
         result['serving'] = dict(error=repr(e))
   elif world == 1 and args.ingest == 'pinned' and headline:
     result['ingest'] = ingest_record(dev, args.steps)
-  if world == 1 and not args.no_cpu_baseline and not args.quick:
+  if world == 1 and args.full and not args.no_cpu_baseline and not args.quick:
     from oracle import cpu_learner
     T1 = T + 1
     # BASELINE.md section 3 protocol: 3 warm-up steps, median of >= 10 timed steps, all host cores
@@ -803,27 +863,28 @@ def main():
                       T, cb, 'the benched configuration itself' if cb == B else 'a bounded sample of the workload: whole columns, same T',
                       CW, CS, sec, os.cpu_count(), thr)}
     result['speedup_vs_cpu_baseline'] = round(rec['frames_per_s'] / fps, 1)
-  # the numbers the driver's tail (last ~2000 characters of stdout) must keep: repeated compactly as the LAST key
-  tail = {'cfg2': dict(ms_per_step=result['ms_per_step'], env_frames_per_s=result['value'],
-                       dominant=roofline['kernel'], frac=roofline['frac'], step_frac=rec['step_roofline']['frac'],
-                       step_floor_ms=rec['step_roofline']['floor_ms'])}
-  for name, key in (('dmlab', 'cfg3'), ('r2d2', 'cfg5')):
-    o = result.get('other_configs', {}).get(name)
-    if o and 'ms_per_step' in o:
-      tail[key] = dict(ms_per_step=o['ms_per_step'], env_frames_per_s=o['env_frames_per_s'],
-                       dominant=o['roofline']['kernel'], frac=o['roofline']['frac'], step_frac=o.get('step_roofline', {}).get('frac'))
-    elif o:
-      tail[key] = dict(error=o.get('error'))
-  sv = result.get('serving') or {}
-  if 'inprocess' in sv:
-    tail['serving'] = dict(inprocess=sv['inprocess'].get('env_steps_per_s_served'),
-                           transport=(sv.get('transport') or {}).get('env_steps_per_s_served'))
-  if 'cpu_baseline' in result:
-    tail['cpu_baseline'] = dict(value=result['cpu_baseline']['value'], B=cb, speedup=result['speedup_vs_cpu_baseline'])
-  if result.get('exchange'):
-    tail['exchange'] = dict(backend=result['exchange']['backend'], ranks=result['exchange']['ranks'],
-                            exposed_ms_per_step=result['exchange']['exposed_ms_per_step'])
-  result['tail_summary'] = tail
+  if args.full:
+    # the numbers the driver's tail (last ~2000 characters of stdout) must keep: repeated compactly as the LAST key
+    tail = {'cfg2': dict(ms_per_step=result['ms_per_step'], env_frames_per_s=result['value'],
+                         dominant=roofline['kernel'], frac=roofline['frac'], step_frac=rec['step_roofline']['frac'],
+                         step_floor_ms=rec['step_roofline']['floor_ms'])}
+    for name, key in (('dmlab', 'cfg3'), ('r2d2', 'cfg5')):
+      o = result.get('other_configs', {}).get(name)
+      if o and 'ms_per_step' in o:
+        tail[key] = dict(ms_per_step=o['ms_per_step'], env_frames_per_s=o['env_frames_per_s'],
+                         dominant=o['roofline']['kernel'], frac=o['roofline']['frac'], step_frac=o.get('step_roofline', {}).get('frac'))
+      elif o:
+        tail[key] = dict(error=o.get('error'))
+    sv = result.get('serving') or {}
+    if 'inprocess' in sv:
+      tail['serving'] = dict(inprocess=sv['inprocess'].get('env_steps_per_s_served'),
+                             transport=(sv.get('transport') or {}).get('env_steps_per_s_served'))
+    if 'cpu_baseline' in result:
+      tail['cpu_baseline'] = dict(value=result['cpu_baseline']['value'], B=cb, speedup=result['speedup_vs_cpu_baseline'])
+    if result.get('exchange'):
+      tail['exchange'] = dict(backend=result['exchange']['backend'], ranks=result['exchange']['ranks'],
+                              exposed_ms_per_step=result['exchange']['exposed_ms_per_step'])
+    result['tail_summary'] = tail
   # the process group is torn down BEFORE the line is printed: RCCL writes to stdout on teardown ("Librccl path : ...")
   # and the JSON line must stay the last line
   if distributed:

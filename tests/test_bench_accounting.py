@@ -77,3 +77,35 @@ def test_kernel_source_digest_tracks_the_sources(tmp_path, monkeypatch):
   with open(dst / 'adam.hip', 'a') as f:
     f.write('// touched\n')
   assert build.csrc_digest() != d1
+
+
+def test_dumped_step_outputs_are_float_arrays_within_the_budget(tmp_path):
+  """--dump-outputs: loss, logged scalars, parameters and gradients as float32 / float64 .npy files; an array above the
+  per-array cap is written as a FIXED sample (the same elements on every run) so that two builds compare element for
+  element, and the whole dump stays under 64 MB."""
+  import collections
+  import types
+  import numpy as np
+  import torch
+  bench = importlib.import_module('bench')
+  n_big = bench.MAX_DUMP_ELEMS + 12345
+  flat = types.SimpleNamespace(params=torch.arange(n_big, dtype=torch.float32), grads=torch.ones(1000))
+  agent = types.SimpleNamespace(flat=flat)
+  session = collections.OrderedDict([('losses/total', torch.tensor(1.5)), ('policy/kl(old|new)', torch.tensor(0.25))])
+  out = bench.step_outputs('atari', (torch.tensor(1.5), session), agent, 'hip-graph')
+  assert set(out) == {'loss', 'log_losses_total', 'log_policy_kl_old_new_', 'params', 'grads'}
+  assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+  assert out['params'].size == bench.MAX_DUMP_ELEMS and np.all(np.diff(out['params']) > 0)
+  again = bench.step_outputs('atari', (torch.tensor(1.5), session), agent, 'hip-graph')
+  np.testing.assert_array_equal(out['params'], again['params'])
+  # R2D2 hands back (loss, priorities, sum of squares) from the graph and (loss, priorities, norm) eagerly: one grad_norm
+  r2 = bench.step_outputs('r2d2', (torch.tensor(2.0), torch.arange(4, dtype=torch.int32), torch.tensor([9.0])), agent,
+                          'hip-graph')
+  assert float(r2['grad_norm']) == 3.0 and r2['priorities'].dtype == np.float64
+  assert float(bench.step_outputs('r2d2', (torch.tensor(2.0), torch.zeros(4), torch.tensor(3.0)), agent,
+                                  'eager')['grad_norm']) == 3.0
+  bench.write_outputs(str(tmp_path / 'dump'), out)
+  names = sorted(os.listdir(tmp_path / 'dump'))
+  assert names == sorted(k + '.npy' for k in out)
+  assert sum(os.path.getsize(tmp_path / 'dump' / f) for f in names) <= 64e6
+  np.testing.assert_array_equal(np.load(tmp_path / 'dump' / 'params.npy'), out['params'])

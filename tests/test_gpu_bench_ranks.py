@@ -28,7 +28,7 @@ def _json_lines(out):
 
 
 def test_bench_two_ranks_gloo_dry_run(device):
-  r = _run('--gpus', '2', '--backend', 'gloo', '--steps', '3', '--warmup', '3', '--quick', '--batch', '32')
+  r = _run('--gpus', '2', '--backend', 'gloo', '--steps', '3', '--warmup', '3', '--full', '--quick', '--batch', '32')
   assert r.returncode == 0, r.stderr[-2000:]
   lines = _json_lines(r.stdout)
   assert len(lines) == 1, r.stdout[-2000:]                      # rank 0 prints ONE line

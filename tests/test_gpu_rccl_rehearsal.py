@@ -103,7 +103,7 @@ def test_bench_force_exchange_on_rccl():
   import json
   env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0', MASTER_PORT=str(_free_port()))
   r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--backend', 'nccl',
-                      '--force-exchange', '--quick', '--steps', '5', '--warmup', '3', '--batch', '64'],
+                      '--force-exchange', '--full', '--quick', '--steps', '5', '--warmup', '3', '--batch', '64'],
                      env=env, capture_output=True, text=True, timeout=900)
   assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
   line = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith('{')][-1])

@@ -1,10 +1,10 @@
 #!/bin/bash
 # Same-box A/B of two builds of libseedhip.so on the cfg2 step: tools/ab_quick.sh <other-lib.so> [rounds]
-# (bench.py --quick, alternating; prints ms_per_step of the six windows and the attributed kernel times)
+# (bench.py --full --quick, alternating; prints ms_per_step of the six windows and the attributed kernel times)
 other=$1; rounds=${2:-2}
 for r in $(seq 1 $rounds); do
   for lib in "" "$other"; do
-    SEEDHIP_LIB=$lib python bench.py --quick 2>/dev/null | python -c "
+    SEEDHIP_LIB=$lib python bench.py --full --quick 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
 k=d['kernels_ms_per_step']

@@ -9,9 +9,9 @@ for v in rne trunc; do
   python -m pytest tests/test_gpu_fullsize.py -q -k "cfg3_dmlab_T20_B256" > $OUT/$v.pytest.log 2>&1
   tail -3 $OUT/$v.pytest.log
   cp $R/gpurun_out/fullsize_parity.jsonl $OUT/$v.parity.jsonl 2>/dev/null
-  python bench.py --quick 2>/dev/null | tail -1 > $OUT/$v.cfg2.json
-  python bench.py --quick --config dmlab 2>/dev/null | tail -1 > $OUT/$v.cfg3.json
-  python bench.py --quick --config r2d2 2>/dev/null | tail -1 > $OUT/$v.cfg5.json
+  python bench.py --full --quick 2>/dev/null | tail -1 > $OUT/$v.cfg2.json
+  python bench.py --full --quick --config dmlab 2>/dev/null | tail -1 > $OUT/$v.cfg3.json
+  python bench.py --full --quick --config r2d2 2>/dev/null | tail -1 > $OUT/$v.cfg5.json
 done
 python - <<PY
 import json

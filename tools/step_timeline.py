@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """One replay of the train step's HIP graph as a timeline: kernel, start offset, duration, idle gap in front of it.
 
-  rocprofv3 --kernel-trace --output-format csv -d <dir> -o t -- python bench.py --quick
+  rocprofv3 --kernel-trace --output-format csv -d <dir> -o t -- python bench.py --full --quick
   python tools/step_timeline.py <dir>/.../t_kernel_trace.csv [first-kernel-substring]
 
 Takes the LAST complete run of kernels between two dispatches whose name contains the first-kernel substring (default:
