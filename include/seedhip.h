@@ -79,6 +79,7 @@ enum {
   SEEDHIP_LOSS_MAX_ACTION_ABS = 9, /* logged :152-153 */
   SEEDHIP_LOSS_ENTROPY_COST = 10,  /* logged :155 (agent.entropy_cost()) */
   SEEDHIP_LOSS_ENTROPY_ADJUSTMENT = 11, /* :128-132 */
+  SEEDHIP_LOSS_POLICY_STD = 12, /* logged :151-152 (mean sigma); written by the tanh-Gaussian head only */
   SEEDHIP_LOSS_NUM = 16
 };
 size_t seedhip_impala_loss_workspace_bytes(int T, int B);
@@ -109,6 +110,43 @@ int seedhip_impala_loss_fwd_bwd_adaptive(
     float max_abs_reward, float clip_rho_threshold, float clip_pg_rho_threshold,
     float mean_denominator, float* d_policy_logits, float* d_baseline, float* vs, float* pg_advantages,
     float* scalars, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- tanh-Gaussian policy (continuous Box actions) -----------------------------------
+ * normal_tanh_distribution of common/parametric_distribution.py:124-202: a parameter row is [loc(D) | s(D)],
+ * sigma = softplus(s) + 1e-3, a = tanh(N(loc, sigma)); log_prob clips the action to +-0.999 and gives the two clipped
+ * ends the averaged tail mass (log_cdf / log_survival - log(1 - 0.999)); the entropy is the reference's single-sample
+ * estimate 0.5 log(2 pi e sigma^2) + log(1 - tanh^2(loc + sigma eps)) summed over D, with eps supplied by the caller.
+ * 1 <= D <= 64 everywhere.
+ *
+ * The fused V-trace loss head: seedhip_impala_loss_fwd_bwd{,_adaptive} with
+ *   learner_params [T+1, B] rows of stride logits_ld >= 2 D (d_params alike; columns 2 D .. logits_ld - 1 are not written),
+ *   behaviour_params [T+1, B, 2 D], actions [T+1, B, D] float in [-1, 1], entropy_noise [T, B, D] standard-normal draws.
+ * entropy_cost_param NULL: the fixed entropy_cost (has_target_entropy must be 0, d_entropy_cost_param NULL); non-NULL:
+ * the learnable cost exp(speed * param) with the semantics of the _adaptive entry point (entropy_cost is ignored).
+ * Gradients wrt loc and s (none wrt the action); scalars as above plus SEEDHIP_LOSS_POLICY_STD; MAX_ACTION_ABS is
+ * max |a|.  Workspace: seedhip_impala_loss_workspace_bytes(T, B). */
+int seedhip_normal_tanh_loss_fwd_bwd(
+    const float* learner_params, int logits_ld, const float* learner_baseline, int baseline_ld,
+    const float* behaviour_params, const float* actions, const float* entropy_noise,
+    const float* rewards, const uint8_t* done, int T, int B, int D,
+    float entropy_cost, const float* entropy_cost_param, float entropy_cost_adjustment_speed, int has_target_entropy,
+    float target_entropy, float* d_entropy_cost_param,
+    float baseline_cost, float kl_cost, float discounting, float lambda_,
+    float max_abs_reward, float clip_rho_threshold, float clip_pg_rho_threshold,
+    float mean_denominator, float* d_params, float* d_baseline, float* vs, float* pg_advantages,
+    float* scalars, void* workspace, size_t workspace_bytes, void* stream);
+/* log_prob [rows] (needs actions [rows, D]) and / or the entropy estimate [rows] (needs noise [rows, D]) of
+ * params [rows, 2 D]; either output may be NULL.  rows == 0 returns at once. */
+int seedhip_normal_tanh_log_prob_entropy(const float* params, const float* actions, const float* noise,
+                                         long long rows, int D, float* log_prob, float* entropy, void* stream);
+/* actions_f32[r, d] = tanh(loc + sigma * eps) for params rows of stride ld >= 2 D; eps is a Box-Muller transform of the
+ * Philox4x32-10 stream keyed by (seed, call, row, d): equal (seed, counter) in rng_state give equal actions, and the call
+ * advances the counter itself (as seedhip_categorical_sample). */
+int seedhip_normal_tanh_sample(const float* params, int ld, long long rows, int D,
+                               unsigned long long* rng_state, float* actions_f32, void* stream);
+/* out[0 .. n) ~ N(0, 1) from the same generator (keyed by (seed, call, i / 4)); advances the counter.  The learner draws
+ * the entropy noise of the loss head with it, inside captured graphs included. */
+int seedhip_normal_fill(float* out, long long n, unsigned long long* rng_state, void* stream);
 
 /* CRC32C (Castagnoli) of a HOST buffer, continuing from `crc` (0 to start): the checksum TensorFlow's checkpoint
  * bundles carry (tensorflow/core/lib/hash/crc32c.h); lets tf_checkpoint.py read / write tf.train.Checkpoint files of the

@@ -77,6 +77,14 @@ SIGNATURES = {
                  P, c_float, c_int, c_float, P,
                  c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_float,
                  P, P, P, P, P, P, c_size_t, P]),
+    'seedhip_normal_tanh_loss_fwd_bwd':
+        (c_int, [P, c_int, P, c_int, P, P, P, P, P, c_int, c_int, c_int,
+                 c_float, P, c_float, c_int, c_float, P,
+                 c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_float,
+                 P, P, P, P, P, P, c_size_t, P]),
+    'seedhip_normal_tanh_log_prob_entropy': (c_int, [P, P, P, c_ll, c_int, P, P, P]),
+    'seedhip_normal_tanh_sample': (c_int, [P, c_int, c_ll, c_int, P, P, P]),
+    'seedhip_normal_fill': (c_int, [P, c_ll, P, P]),
     'seedhip_adam_flat': (c_int, [P, P, P, P, c_ll, c_float, c_float, c_float, c_float, c_float,
                                   c_ll, c_float, c_float, P]),
     'seedhip_adam_flat_dev_lr': (c_int, [P, P, P, P, c_ll, P, c_float, c_float, c_float, c_float,

@@ -51,11 +51,23 @@ def pack_request(n, env_ids, run_ids, reward, raw_reward, done, abandoned=None, 
   return buf
 
 
+def require_categorical(agent, what):
+  """Central inference keeps actions in scalar int64 tables (previous-action table, unroll store, gRPC action tensors);
+  a continuous distribution's float [.., D] actions do not fit them."""
+  dist = getattr(agent, 'action_distribution', None)
+  kind = getattr(dist, 'loss_head', 'categorical') if dist is not None else 'categorical'
+  if kind != 'categorical':
+    raise NotImplementedError('%s: central inference stores scalar int64 actions; an agent with a %r action '
+                              'distribution can be trained (learner.compute_loss / Learner / GraphedStep) but not '
+                              'served' % (what, kind))
+
+
 class InferenceState(object):
   """The per-host state the reference builds in create_host (learner.py:314-336)."""
 
   def __init__(self, agent, num_envs, unroll_length, env_output_specs, agent_output_specs, action_spec,
                num_action_repeats=1, device='cuda', unroll_sink=None, info_sink=None):
+    require_categorical(agent, 'InferenceState')
     self.agent, self.num_envs, self.unroll_length = agent, num_envs, unroll_length
     self.num_action_repeats = num_action_repeats
     self.device = torch.device(device)
@@ -136,6 +148,7 @@ class FusedInferenceState(object):
 
   def __init__(self, agent, num_envs, unroll_length, env_output_specs, agent_output_specs, batch_capacity,
                num_action_repeats=1, device='cuda', stats_capacity=4096):
+    require_categorical(agent, 'FusedInferenceState')
     self.agent, self.E, self.L = agent, num_envs, unroll_length + 1
     self.cap, self.num_action_repeats = batch_capacity, num_action_repeats
     self.device = dev = torch.device(device)

@@ -51,6 +51,39 @@ class DictLogger(object):
     session[name] = value
 
 
+def _categorical_loss_head(dist, agent, agent_outputs, flat_head, flat_dhead, ldh, rewards, done_u8, T, B, scalars, ws,
+                           vs, pg, kw):
+  A = dist.param_size
+  beh_logits = agent_outputs.policy_logits.to(torch.float32).contiguous()
+  actions = agent_outputs.action.contiguous()
+  if actions.dtype not in (torch.int32, torch.int64):
+    actions = actions.to(torch.int64)
+  ops.impala_loss_fwd_bwd(flat_head, ldh, flat_head[A:], ldh, beh_logits, actions, rewards, done_u8, T, B, A,
+                          flat_dhead, flat_dhead[A:], scalars, ws, vs, pg, **kw)
+  return ()
+
+
+def _normal_tanh_loss_head(dist, agent, agent_outputs, flat_head, flat_dhead, ldh, rewards, done_u8, T, B, scalars, ws,
+                           vs, pg, kw):
+  """Continuous actions: float actions [T+1, B, D], behaviour parameters [T+1, B, 2 D], and the standard-normal draws of
+  the single-sample entropy estimate, drawn on the device from the distribution's own generator."""
+  D, P = dist.num_actions, dist.param_size
+  if ldh < P + 1:
+    raise ValueError('the agent\'s head row (%d columns) does not hold %d distribution parameters + baseline' % (ldh, P))
+  beh = agent_outputs.policy_logits.to(torch.float32).contiguous()
+  actions = agent_outputs.action.to(torch.float32).contiguous()
+  if tuple(beh.shape) != (T + 1, B, P) or tuple(actions.shape) != (T + 1, B, D):
+    raise ValueError('normal_tanh loss: behaviour parameters %s / actions %s, expected %s / %s'
+                     % (tuple(beh.shape), tuple(actions.shape), (T + 1, B, P), (T + 1, B, D)))
+  noise = dist.draw_noise((T, B, D), flat_head.device, out=agent._buf('entropy_noise', (T, B, D)))
+  ops.normal_tanh_loss_fwd_bwd(flat_head, ldh, flat_head[P:], ldh, beh, actions, noise, rewards, done_u8, T, B, D,
+                               flat_dhead, flat_dhead[P:], scalars, ws, vs, pg, **kw)
+  return (('policy/std', 12),)                        # learner.py:151-152
+
+
+LOSS_HEADS = {'categorical': _categorical_loss_head, 'normal_tanh': _normal_tanh_loss_head}
+
+
 def compute_loss(logger, parametric_action_distribution, agent, agent_state, prev_actions, env_outputs,
                  agent_outputs, config=None, mean_denominator=None, want_vtrace=False):
   """learner.py:73-159.  Runs the agent unroll and the fused loss head; the head
@@ -64,12 +97,7 @@ def compute_loss(logger, parametric_action_distribution, agent, agent_state, pre
   head, d_head, ldh = agent.head_buffers()
   T1, B = env_outputs.done.shape[0], env_outputs.done.shape[1]
   T = T1 - 1
-  A = parametric_action_distribution.param_size
   dev = head.device
-  beh_logits = agent_outputs.policy_logits.to(torch.float32).contiguous()
-  actions = agent_outputs.action.contiguous()
-  if actions.dtype not in (torch.int32, torch.int64):
-    actions = actions.to(torch.int64)
   rewards = env_outputs.reward.to(torch.float32).contiguous()
   done_u8 = ops.as_u8(env_outputs.done)
   scalars = agent._buf('loss_scalars', (16,))
@@ -91,18 +119,20 @@ def compute_loss(logger, parametric_action_distribution, agent, agent_state, pre
       raise ValueError('target_entropy needs the learnable entropy cost: construct the agent without its own '
                        'entropy_cost and pass it to a Learner (agents/vtrace/learner.py:225-234)')
     ekw = dict(entropy_cost=float(cfg.entropy_cost if own is None else own))
-  flat_head = head.view(-1)
-  flat_dhead = d_head.view(-1)
-  ops.impala_loss_fwd_bwd(
-      flat_head, ldh, flat_head[A:], ldh, beh_logits, actions, rewards, done_u8, T, B, A,
-      flat_dhead, flat_dhead[A:], scalars, ws, vs, pg,
-      baseline_cost=cfg.baseline_cost, kl_cost=cfg.kl_cost,
-      discounting=cfg.discounting, lambda_=cfg.lambda_, max_abs_reward=cfg.max_abs_reward,
-      mean_denominator=mean_denominator, **ekw)
+  ekw.update(baseline_cost=cfg.baseline_cost, kl_cost=cfg.kl_cost, discounting=cfg.discounting, lambda_=cfg.lambda_,
+             max_abs_reward=cfg.max_abs_reward, mean_denominator=mean_denominator)
+  # the distribution names its fused loss head (the reference's compute_loss is distribution-agnostic, learner.py:95-98)
+  kind = getattr(parametric_action_distribution, 'loss_head', 'categorical')
+  if kind not in LOSS_HEADS:
+    raise NotImplementedError('no fused loss head for a %r distribution (have: %s)' % (kind, ', '.join(sorted(LOSS_HEADS))))
+  extra = LOSS_HEADS[kind](parametric_action_distribution, agent, agent_outputs, head.view(-1), d_head.view(-1), ldh,
+                           rewards, done_u8, T, B, scalars, ws, vs, pg, ekw)
   session = logger.log_session()
   for name, idx in LOGGED.items():
     logger.log(session, name, scalars[idx])
   logger.log(session, 'policy/entropy_cost', scalars[10])
+  for name, idx in extra:
+    logger.log(session, name, scalars[idx])
   if want_vtrace:
     session['vtrace/vs'] = vs
     session['vtrace/pg_advantages'] = pg

@@ -267,15 +267,25 @@ class _Agent(object):
   def _sample(self, head, rows):
     """tfd.Categorical(logits).sample() of the reference heads (dmlab/networks.py:122): one kernel over the head-GEMM
     output rows [rows, ldh] (logits in columns 0..A-1), Gumbel-max over counter-based randoms."""
+    dist = self.action_distribution
+    if dist is not None and getattr(dist, 'loss_head', 'categorical') != 'categorical':
+      return dist.sample_rows(head, self._ldh, rows, self.rng_state())       # continuous: float32 [rows, D]
     action = torch.empty(rows, dtype=torch.int64, device=self.device)
     ops.categorical_sample(head, self._ldh, rows, self._num_actions, self.rng_state(), action)
     return action
 
+  # the distribution object an agent was constructed with (MLPandLSTM, like agents/vtrace/networks.py); None = the
+  # categorical head over `num_actions` logits that every agent constructed with an int has
+  action_distribution = None
+
   def _agent_output(self, head, T1, B, sample):
-    A = self._num_actions
+    A = self._num_actions                            # width of the policy head: logits, or distribution parameters
     h3 = head.view(T1, B, self._ldh)
     logits, baseline = h3[..., :A], h3[..., A]
-    action = self._sample(head, T1 * B).view(T1, B) if sample else None
+    action = None
+    if sample:
+      action = self._sample(head, T1 * B)
+      action = action.view((T1, B) + tuple(action.shape[1:]))
     return AgentOutput(action, logits, baseline)
 
 
@@ -1025,9 +1035,16 @@ class MLPandLSTM(_Agent):
   unroll (a layer only needs its own previous state and the layer below at the same step), each on the whole-sequence
   LSTM kernels; state = tuple of (h, c) per cell (StackedRNNCells.get_initial_state)."""
 
-  def __init__(self, num_actions, observation_size, mlp_sizes=(64, 64), lstm_sizes=(64,), device='cuda', seed=0,
-               entropy_cost=None):
+  def __init__(self, parametric_action_distribution, observation_size, mlp_sizes=(64, 64), lstm_sizes=(64,),
+               device='cuda', seed=0, entropy_cost=None):
+    """parametric_action_distribution: a distribution object (the reference's constructor, networks.py:28-29: the
+    policy head has `param_size` columns and actions come from `distribution.sample`: float32 [.., D] for
+    normal_tanh_distribution), or an int = that many categorical actions."""
+    dist = parametric_action_distribution
+    num_actions = dist if isinstance(dist, int) else dist.param_size
     super(MLPandLSTM, self).__init__(num_actions, device)
+    if not isinstance(dist, int):
+      self.action_distribution = dist
     if not lstm_sizes:
       raise ValueError('MLPandLSTM needs at least one LSTM layer')
     if any(m % 4 for m in mlp_sizes) or any(h % 4 for h in lstm_sizes):

@@ -405,6 +405,78 @@ def impala_loss_fwd_bwd(logits, logits_ld, baseline, baseline_ld, beh_logits, ac
           'seedhip_impala_loss_fwd_bwd')
 
 
+def normal_tanh_loss_fwd_bwd(params, logits_ld, baseline, baseline_ld, beh_params, actions, noise, rewards, done_u8,
+                             T, B, D, d_params, d_baseline, scalars, workspace, vs=None, pg=None,
+                             entropy_cost=0.00025, baseline_cost=0.5, kl_cost=0.0, discounting=0.99,
+                             lambda_=1.0, max_abs_reward=0.0, clip_rho=1.0, clip_pg_rho=1.0,
+                             mean_denominator=None, entropy_cost_param=None, d_entropy_cost_param=None,
+                             entropy_cost_adjustment_speed=10.0, target_entropy=None):
+  """The fused V-trace loss head of the tanh-Gaussian policy (csrc/loss_normal_tanh.hip); arguments as
+  impala_loss_fwd_bwd with float actions [T+1, B, D], behaviour parameters [T+1, B, 2 D] and the entropy noise [T, B, D]."""
+  n = float(T * B if mean_denominator is None else mean_denominator)
+  for name, t, numel in (('beh_params', beh_params, (T + 1) * B * 2 * D), ('actions', actions, (T + 1) * B * D),
+                         ('noise', noise, T * B * D), ('rewards', rewards, (T + 1) * B), ('done', done_u8, (T + 1) * B)):
+    if t.numel() != numel:
+      raise ValueError('normal_tanh_loss: %s has %d elements, expected %d' % (name, t.numel(), numel))
+  for name, t in (('beh_params', beh_params), ('actions', actions), ('noise', noise), ('rewards', rewards)):
+    if t.dtype != torch.float32:
+      raise ValueError('normal_tanh_loss: %s must be float32, got %s' % (name, t.dtype))
+  if done_u8.element_size() != 1:
+    raise ValueError('normal_tanh_loss: done must be one byte per element')
+  last = ((T + 1) * B - 1)
+  if params.numel() < last * logits_ld + 2 * D or d_params.numel() < last * logits_ld + 2 * D or \
+      baseline.numel() < last * baseline_ld + 1 or d_baseline.numel() < last * baseline_ld + 1:
+    raise ValueError('normal_tanh_loss: parameter / baseline buffers too small for [T+1, B] rows of the given strides')
+  if scalars.numel() < 16 or (vs is not None and vs.numel() < T * B) or (pg is not None and pg.numel() < T * B):
+    raise ValueError('normal_tanh_loss: scalars / vs / pg buffers too small')
+  _lib.require_cuda(beh_params, actions, noise, rewards, done_u8)
+  with _region('normal_tanh_loss', 0, T * B * (32 * D + 25)):
+    with _dev(scalars):
+      _lib.check(_lib.lib().seedhip_normal_tanh_loss_fwd_bwd(
+          _lib.ptr(params), logits_ld, _lib.ptr(baseline), baseline_ld, _lib.ptr(beh_params), _lib.ptr(actions),
+          _lib.ptr(noise), _lib.ptr(rewards), _lib.ptr(done_u8), T, B, D,
+          float(entropy_cost), _lib.ptr(entropy_cost_param), float(entropy_cost_adjustment_speed),
+          int(bool(target_entropy)), float(target_entropy or 0.0), _lib.ptr(d_entropy_cost_param),
+          baseline_cost, kl_cost, discounting, lambda_, max_abs_reward, clip_rho, clip_pg_rho,
+          n, _lib.ptr(d_params), _lib.ptr(d_baseline), _lib.ptr(vs), _lib.ptr(pg), _lib.ptr(scalars),
+          _lib.ptr(workspace), workspace.numel() * workspace.element_size(), _lib.stream()),
+          'seedhip_normal_tanh_loss_fwd_bwd')
+
+
+def normal_tanh_log_prob_entropy(params, actions, noise, rows, D, log_prob, entropy):
+  """log_prob [rows] and / or the entropy estimate [rows] of params [rows, 2 D] (actions / noise [rows, D])."""
+  for t, numel in ((params, rows * 2 * D), (actions, rows * D), (noise, rows * D), (log_prob, rows), (entropy, rows)):
+    if t is not None and (t.numel() != numel or t.dtype != torch.float32):
+      raise ValueError('normal_tanh_log_prob_entropy: float32 tensor of %d elements expected, got %s of %d'
+                       % (numel, t.dtype, t.numel()))
+  _lib.require_cuda(params, actions, noise, log_prob, entropy)
+  with _dev(params):
+    _lib.check(_lib.lib().seedhip_normal_tanh_log_prob_entropy(
+        _lib.ptr(params), _lib.ptr(actions), _lib.ptr(noise), rows, D, _lib.ptr(log_prob), _lib.ptr(entropy),
+        _lib.stream()), 'seedhip_normal_tanh_log_prob_entropy')
+
+
+def normal_tanh_sample(params, ld, rows, D, rng_state, actions):
+  """actions[r, d] = tanh(loc + sigma * eps) for parameter rows of stride ld (Box-Muller over Philox randoms; advances
+  rng_state[1])."""
+  if rows and (params.numel() < (rows - 1) * ld + 2 * D or actions.numel() != rows * D or actions.dtype != torch.float32
+               or params.dtype != torch.float32):
+    raise ValueError('normal_tanh_sample: params / actions do not hold %d rows of D = %d (ld = %d) float32' % (rows, D, ld))
+  with _dev(actions):
+    _lib.check(_lib.lib().seedhip_normal_tanh_sample(_lib.ptr(params), ld, rows, D, _lib.ptr(rng_state),
+                                                     _lib.ptr(actions), _lib.stream()), 'seedhip_normal_tanh_sample')
+
+
+def normal_fill(out, rng_state):
+  """out ~ N(0, 1) elementwise from the (seed, counter) device generator rng_state (advances the counter)."""
+  if out.dtype != torch.float32:
+    raise ValueError('normal_fill: float32 output expected, got %s' % out.dtype)
+  _lib.require_cuda(out)
+  with _dev(out):
+    _lib.check(_lib.lib().seedhip_normal_fill(_lib.ptr(out), out.numel(), _lib.ptr(rng_state), _lib.stream()),
+               'seedhip_normal_fill')
+
+
 def adam_flat(params, grads, m, v, lr_t, beta_1, beta_2, epsilon, grad_scale=1.0, clamp=None, guard=None):
   """clamp = (index, lo, hi): params[index] is clipped to [lo, hi] after its update (Keras variable constraint).
   guard: int32[1] device tensor; non-zero on the device = the update is skipped (seedhip_adam_flat_guarded)."""
